@@ -9,8 +9,15 @@ pivots"), on inputs already resident in HBM.  `value` is simplex pivots/s of
 the whole job: every rank solves its own replica (seed 42 + rank), so per-GPU
 work is fixed as N grows ("scaling": "weak", replicas only for a single LP).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 (torchrun-launched for N > 1; RANK/LOCAL_RANK/WORLD_SIZE from the env).
+
+A plain run does what the headline needs and no more: set-up, W warm-up steps,
+K timed steps, the result line.  --dump-outputs DIR writes what the last timed
+step returned to its caller (DIR/<name>.npy, float64).  --full adds, after the
+timed region, everything else the bench measures: the roofline and event
+passes, the per-kernel timings, the CPU baseline (--no-cpu leaves it out) and
+the secondary configurations (--no-extra leaves them out).
 """
 from __future__ import annotations
 
@@ -84,6 +91,18 @@ def log(rank, *a):
         print(*a, file=sys.stderr, flush=True)
 
 
+def dump_outputs(dirname, rank, ret, res):
+    """What the last timed glp_simplex call handed back (GkProblem.result():
+    statuses, primal and dual values of rows and columns, objective, iteration
+    count, and the call's return code), one float64 array per name; about
+    1 MB for C3.  Ranks other than 0 write <name>.rank<r>.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+    for name, v in dict(res, ret=ret).items():
+        np.save(os.path.join(dirname, name + sfx + ".npy"), np.atleast_1d(np.asarray(v, dtype=np.float64)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -93,9 +112,16 @@ def main():
     ap.add_argument("--m", type=int, default=4096)
     ap.add_argument("--n", type=int, default=16384)
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="bounded CPU-baseline sample (oracle)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave the secondary configurations out")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the roofline / event passes, the per-kernel timings, the CPU "
+                         "baseline and the secondary configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -143,6 +169,7 @@ def main():
     log(rank, f"[bench] generated C3 {args.m}x{args.n} in {time.time() - t_gen:.1f}s")
 
     restarts = [0]
+    last = {"ret": None, "at_optimum": None}
 
     def step(tag="headline"):
         it0 = P.it_cnt
@@ -150,7 +177,9 @@ def main():
         ret = gk.glp_simplex(P, parm)
         if ret not in (0, 8):
             raise RuntimeError(f"glp_simplex returned {ret}")
+        last["ret"], last["at_optimum"] = ret, None
         if ret == 0:                    # optimum reached: restart from the slack basis
+            last["at_optimum"] = P.result()         # (what this call returned, before the restart overwrites it)
             P.row_stat[1:] = problems.GLP_BS
             P.col_stat[1:] = problems.GLP_NL
             P.valid = 0
@@ -193,6 +222,8 @@ def main():
     dt = time.perf_counter() - t0
     ctx.mark(2)                         # timed region ends
     st = P.stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, last["ret"], last["at_optimum"] or P.result())
 
     # roofline pass: the same steps again (continuing), with the pivot
     # kernels' device-clock stamps and byte accounting on (gk_bfd_profile(4):
@@ -200,7 +231,7 @@ def main():
     # the timed region), graphs kept as in the timed region
     dev = {"ms": 0.0, "ms_b": 0.0, "launches": 0, "bytes": 0.0, "ms_r": 0.0, "launches_r": 0, "bytes_pivots": 0.0,
            "upd_ms": 0.0, "upd_launches": 0, "upd_bytes": 0.0, "pivots": 0}
-    if rank == 0:
+    if rank == 0 and args.full:
         rewind()
         P.profile(4)
         for _ in range(args.steps):
@@ -224,7 +255,7 @@ def main():
     # start and a stop event on the engine stream — the command processor's
     # timestamps of the dispatch itself, which is what a profiler reports
     trow = {"ms": 0.0, "launches": 0, "bytes": 0.0, "upd_ms": 0.0, "upd_launches": 0}
-    if rank == 0:
+    if rank == 0 and args.full:
         rewind()
         P.profile(True)
         for _ in range(args.steps):
@@ -260,7 +291,7 @@ def main():
     # committed rocprof averages of the same command are reported beside it.
     roof = None
     kern = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         for which, name in ((0, "pivot_row_pass"), (1, "dual_pse_A_w_dense"), (2, "ftran_Binv_x_dense"),
                             (3, "binv_rank1_dense")):
             ms_k, b_k = P.time_kernel(which, reps=10)
@@ -319,7 +350,7 @@ def main():
 
     cpu = None
     extra = {}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import orcpy   # CPU baseline leg only: the bit-faithful C port of the reference
         base = problems.gen_dense(args.m, args.n, seed=42, keep_dense=False)
@@ -349,6 +380,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(1000.0 * max_dt / args.steps, 3),
             "higher_is_better": True,
             "scaling": "weak",
@@ -363,7 +395,8 @@ def main():
             "roofline": roof,
             "cpu_baseline": cpu,
             "engine": {"ms_split_per_step": {k: round(1000.0 * v / args.steps, 3) for k, v in split.items()},
-                       "bytes_per_pivot_roofline_pass": round(dev["bytes_pivots"] / max(1, dev["pivots"])),
+                       "bytes_per_pivot_roofline_pass": round(dev["bytes_pivots"] / max(1, dev["pivots"]))
+                       if args.full else None,
                        "graphs_built_last_step": int(st.graphs_built),
                        "pivots": int(st.pivots), "reinversions_timed_region": reinv,
                        "batches": int(st.batches), "host_syncs": int(st.host_syncs),
@@ -372,7 +405,7 @@ def main():
             "extra": {},
         }
 
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         if world == 1:
             del P
             extra = run_extra(gk, problems, ctx, prob)

@@ -8,7 +8,8 @@
 #   tests:F1,F2      -m gpu tests of the named files (tests/F1 ...)
 #   k:EXPR           -m gpu tests selected by -k EXPR
 #   smoke            __graft_entry__.py smoke
-#   bench            python bench.py (defaults: the driver's command)
+#   bench            python bench.py --full (default sizes, with the roofline,
+#                    CPU-baseline and secondary-configuration legs)
 #   bench:ARGS       python bench.py ARGS (commas for spaces)
 #   profile          tools/profile_round.sh (rocprofv3 stats + PMC passes)
 #   apitrace         rocprofv3 HIP API + kernel + copy traces (CSV) of a short bench
@@ -30,7 +31,7 @@ for step in "$@"; do
                      > "$O/tests_$(echo "$f" | tr ',/' '__').log" 2>&1 ;;
         k:*) timeout -k 10 900 $PYT tests -k "${step#k:}" > "$O/tests_k.log" 2>&1 ;;
         smoke) timeout -k 10 300 python -u __graft_entry__.py smoke > "$O/smoke.log" 2>&1 ;;
-        bench) timeout -k 10 900 python -u bench.py > "$O/bench.json" 2> "$O/bench.err" ;;
+        bench) timeout -k 10 900 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.err" ;;
         bench:*) a=$(echo "${step#bench:}" | tr ',' ' ');
                  timeout -k 10 900 python -u bench.py $a > "$O/bench_args.json" 2> "$O/bench_args.err" ;;
         profile) bash tools/profile_round.sh "$NAME/profile" ;;

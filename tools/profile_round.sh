@@ -17,7 +17,7 @@ OUT=gpurun_out/$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 T=/tmp/prof_$R
-ARGS="--gpus 1 --steps 20 --warmup 5 --no-cpu --no-extra"
+ARGS="--gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-extra"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $T/prof -o run -- python3 bench.py $ARGS > $OUT/prof_bench.json 2> $OUT/prof.err
 python3 tools/prof_stats.py $T/prof/run_results.db --csv $OUT/stats.csv > $OUT/stats_grid.txt
 python3 tools/prof_stats.py $T/prof/run_results.db --marked --csv $OUT/stats_timed.csv --json $OUT/stats_timed.json > /dev/null
