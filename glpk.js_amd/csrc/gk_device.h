@@ -429,8 +429,17 @@ __device__ __forceinline__ Cand no_cand(double k1)
 // 64-slot group of the pivot row), pass-2 candidates (one per wave of
 // k_dual_ratio).  gpart: gamma_p sums of the 64-slot groups [4 gv), then
 // their max |trow| [4 gv).
-__device__ __forceinline__ Cand *cand_pass1(const SpxDev &d) { return (Cand *)d.cand + 4 * gv_of(d.m, d.n); }
-__device__ __forceinline__ Cand *cand_pass2(const SpxDev &d) { return (Cand *)d.cand + 8 * gv_of(d.m, d.n); }
+// The chuzr region holds 4 gv entries or, under k_dual_update, one per 16-row
+// block (ceil(m / 16), more than 4 gv when n < 4 m), whichever is more: the
+// regions must not overlap, since the blocks of the pivot-row kernel read the
+// chuzr candidates at entry while blocks that are further on already store
+// their pass-1 candidates.
+__device__ __forceinline__ int cand_chuzr_cap(int m, int n) { return max(4 * gv_of(m, n), (m + 15) / 16); }
+__device__ __forceinline__ Cand *cand_pass1(const SpxDev &d) { return (Cand *)d.cand + cand_chuzr_cap(d.m, d.n); }
+__device__ __forceinline__ Cand *cand_pass2(const SpxDev &d)
+{
+    return (Cand *)d.cand + cand_chuzr_cap(d.m, d.n) + 4 * gv_of(d.m, d.n);
+}
 __device__ __forceinline__ double *tmax_part(const SpxDev &d) { return d.gpart + 4 * gv_of(d.m, d.n); }
 
 // the choice over cnt stored candidates, made by one wave (lane-strided scan,

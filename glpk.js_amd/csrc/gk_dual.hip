@@ -2669,13 +2669,23 @@ __global__ void __launch_bounds__(1024) k_dual_update(SpxDev d, int gn, int ncb,
     // times the CSC column, one wave
     if (!SP && rl == 0) salp[gs] = al;
     if (SP && w == wa) {
+        // row p of inv(B) is taken from the compact rho k_dual_col published
+        // (rho_val[t] = inv(B)[p, rlist[t]]; the unit columns of the basic
+        // slacks hold 1 at the leaving one and 0 elsewhere), not read from
+        // inv(B): the block that owns row p rewrites it further down, and a
+        // block that gets here later would read the updated row.  The lists
+        // change only behind the gate (books_store), after every block's loads
+        auto rho_at = [&](int c) {
+            const int t = d.rpos[c];
+            return t >= 0 ? d.rho_val[t] : (c == kp - 1 ? 1.0 : 0.0);
+        };
         double s = 0.0;
         if (kq > m) {
             const int cq = kq - m - 1;
             const int beg = d.A.cptr[cq], end = d.A.cptr[cq + 1];
-            for (int t = beg + lane; t < end; t += 64) s += d.A.cval[t] * Bv[(size_t)d.A.cind[t] * ldb + (p - 1)];
+            for (int t = beg + lane; t < end; t += 64) s += d.A.cval[t] * rho_at(d.A.cind[t]);
         } else if (lane == 0) {
-            s = -Bv[(size_t)(kq - 1) * ldb + (p - 1)];
+            s = -rho_at(kq - 1);
         }
         s = wsum(s);
         if (lane == 0) salpha = s;

@@ -539,9 +539,10 @@ static void engine_alloc(Engine &E, int m, int n, gk_ctx *ctx)
             // gv each; primal: max |tcol|, d_q sums, gamma_q sums of the row
             // groups, 16 gv each
             place(E.gpart, 56 * gv);
-            // candidates (24-byte entries): chuzr | pass 1 | pass 2, 4 gv each,
+            // candidates (24-byte entries): chuzr (4 gv, or one per 16 rows
+            // for k_dual_update: cand_chuzr_cap) | pass 1 | pass 2, 4 gv each,
             // then the primal pass-1 candidates of the row groups, 16 gv
-            place(E.cand, 3 * 28 * gv);
+            place(E.cand, 3 * (28 * gv + ((size_t)m + 15) / 16));
             // dual: reference-space non-basic structurals (n); primal: basic
             // slacks in the reference space (m)
             place(E.wlist, (size_t)std::max(m, n) + 1); place(E.wpos, (size_t)std::max(m, n) + 1);
@@ -2168,6 +2169,14 @@ void Spx::init()
         hs = DState{};
         hs.nr = (int)rl.size();
         hs.nwl = 0;
+        sync();
+    }
+    if (parm->pricing != PT_PSE) {
+        // textbook pricing never resets the reference space, so nothing on
+        // the device sets the weights: they are init_csa's ones (glpspx01.js:
+        // 144, glpspx02.js:189), not what the last call left in the buffer
+        const std::vector<double> ones(std::max(m, n), 1.0);
+        HIPCHK(hipMemcpyAsync(E->gamma.p, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice, s));
         sync();
     }
     hs.phase = 0;

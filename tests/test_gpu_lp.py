@@ -12,6 +12,7 @@ import pytest
 
 from conftest import golden_files, load_golden
 from glpk_js_amd import gk, problems
+from lpgen import general_kkt
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +25,9 @@ for path in golden_files("lp_"):
 
 def check_solution(P: gk.GkProblem, tol=1e-7):
     """Primal consistency of the stored solution: row activities equal A x,
-    bounds hold within tolerance, objective equals c'x + c0."""
+    bounds hold within tolerance (when the solution claims primal
+    feasibility: a stopped dual run is primal infeasible by design),
+    objective equals c'x + c0."""
     p = P.p
     x = P.col_prim[1:]
     act = np.zeros(p.m)
@@ -35,6 +38,19 @@ def check_solution(P: gk.GkProblem, tol=1e-7):
     assert np.max(np.abs(act - P.row_prim[1:]), initial=0.0) <= 1e-8 * scale
     obj = p.c0 + float(np.dot(p.col_coef, x))
     assert abs(obj - P.obj_val) <= 1e-9 * max(1.0, abs(obj))
+    if P.pbs_stat == problems.GLP_FEAS:
+        # every row and column inside its own bounds, with the reference's
+        # slack tol_bnd (1 + |bound|)
+        for what, typ, lb, ub, val in (("row", p.row_type, p.row_lb, p.row_ub, P.row_prim[1:]),
+                                       ("column", p.col_type, p.col_lb, p.col_ub, x)):
+            has_lb = np.isin(typ, (problems.GLP_LO, problems.GLP_DB, problems.GLP_FX))
+            has_ub = np.isin(typ, (problems.GLP_UP, problems.GLP_DB, problems.GLP_FX))
+            ub = np.where(typ == problems.GLP_FX, lb, ub)
+            below = has_lb & (val < lb - tol * (1.0 + np.abs(lb)))
+            above = has_ub & (val > ub + tol * (1.0 + np.abs(ub)))
+            assert not below.any() and not above.any(), (
+                f"{what}s outside their bounds: below {np.nonzero(below)[0][:5] + 1}, "
+                f"above {np.nonzero(above)[0][:5] + 1}")
 
 
 @pytest.mark.parametrize("path,run_index", LP_CASES)
@@ -54,6 +70,9 @@ def test_gpu_lp_matches_reference(gpu_ctx, path, run_index):
         ref = run["obj_val"]
         assert abs(P.obj_val - ref) <= 1e-9 * max(1.0, abs(ref)), (P.obj_val, ref)
         check_solution(P)
+        # the full certificate (duals, their signs, complementary slackness):
+        # valid whichever of several degenerate optima the GPU returns
+        general_kkt(P, prob)
 
 
 IT_LIM_CASES = [c for c in LP_CASES if load_golden(c.values[0])["runs"][c.values[1]]["opts"].get("it_lim")]
