@@ -303,6 +303,13 @@ struct TopState {
     double obj;
 };
 
+// ST_CAP: the batch's plan (launch geometry, speculative list loads, the
+// register slots of k_dual_update) serves lists of up to nr_cap entries and a
+// support of rho of as many, and this pivot may add one.  Tested by the
+// kernels that choose p, in the decision code every block evaluates alike.
+// A cap of m cannot be passed (nr <= m, ns <= m)
+__device__ __forceinline__ bool list_full(int nr, int nr_cap, int m) { return nr + 1 > nr_cap && nr_cap < m; }
+
 struct FinishIn {
     int pend, p, q, kp, kq, fxp, rclr, upd_cnt, it_cnt, npiv, rig;
     double delta;
@@ -386,6 +393,24 @@ __device__ __forceinline__ void finish_arrays(const SpxDev &d, const FinishIn &f
         }
     }
     __syncthreads();
+}
+
+// finish_arrays without its block barriers, for one thread of a block whose
+// waves patch the entries below wherever they read them (k_dual_row's lead
+// block on the path of a running pivot): called after the calling wave's own
+// loads of bind / stat / refsp, so program order keeps them apart, and no
+// other wave of the block uses what it loads from these arrays
+__device__ __forceinline__ void finish_arrays_wave0(const SpxDev &d, const FinishIn &f)
+{
+    const int m = d.m;
+    if (f.pend) {
+        d.head[f.p - 1] = f.kq;
+        d.head[m + f.q - 1] = f.kp;
+        d.bind[f.kq - 1] = f.p;
+        d.bind[f.kp - 1] = m + f.q;
+        d.stat[f.q - 1] = f.fxp ? NS : (f.delta > 0.0 ? NL : NU);
+        if (f.rclr) d.refsp[f.kp - 1] = 0;
+    }
 }
 
 __device__ __forceinline__ void finish_scalars(const SpxDev &d, const FinishIn &f, bool refsp_reset)
@@ -556,6 +581,10 @@ __global__ void __launch_bounds__(TOP_WG) k_dual_top(SpxDev d, int rowpath, int 
         if (threadIdx.x == 0) { st->p = 0; st->stop = ST_P0; }
         return;
     }
+    if (rowpath != 3 && list_full(nr, nr_cap, m)) {
+        if (threadIdx.x == 0) st->stop = ST_CAP;
+        return;
+    }
     const int p = best.idx, kp = best.aux;
     if (rowpath == 3) {
         // sparse factor: rho = inv(B)' e_p is the BTRAN that follows
@@ -626,7 +655,7 @@ __global__ void __launch_bounds__(TOP_WG) k_dual_top(SpxDev d, int rowpath, int 
 // (PANEL = 0: no panel pick compiled in, so the plans without the panel do
 // not reserve its 24 KB candidate array in LDS — ADVICE r5)
 template <int PANEL>
-__global__ void __launch_bounds__(256) k_dual_top_grid(SpxDev d, int pcap, int page_max)
+__global__ void __launch_bounds__(256) k_dual_top_grid(SpxDev d, int pcap, int page_max, int nr_cap)
 {
     const TraceScope trace_(d, 0);
     DState *st = d.st;
@@ -656,6 +685,7 @@ __global__ void __launch_bounds__(256) k_dual_top_grid(SpxDev d, int pcap, int p
         why = ST_OBJLIM;
     const Cand best = wave_best<0>(cc);
     if (why == ST_RUN && best.idx == 0) why = ST_P0;
+    if (why == ST_RUN && list_full(nr, nr_cap, m)) why = ST_CAP;
     // every block passes the entry gate before block 0 stores the state
     // (gk_device.h); the header arrays it changes are not read here
     gate_arrive(st);
@@ -935,8 +965,10 @@ __global__ void __launch_bounds__(1024) k_trow_rows(SpxDev d, int pse)
 // 64 slots of the pivot row.  The pending change of basis of the previous
 // pivot is applied by block 0; the other blocks patch the few entries it
 // changes (bind of kp / kq, stat of q, refsp of kp) where they read them, so
-// the race with block 0's writes is benign (the patch is idempotent).  Block
-// 0 also publishes the compact rho (rho_idx / rho_val, read by the commit),
+// the race with block 0's writes is benign (the patch is idempotent).  The
+// writer block patches its own reads the same way, so on the path of a running
+// pivot it applies the change without a block barrier (finish_arrays_wave0).
+// It also publishes the compact rho (rho_idx / rho_val, read by the commit),
 // the scalar state and, every 1000 pivots, the reference-space reset.
 // ---------------------------------------------------------------------------
 // NP: list entries per wave loaded in trips 1-2 (8, or 16 when ns may exceed
@@ -1003,6 +1035,7 @@ __global__ void __launch_bounds__(1024) k_dual_row(SpxDev d, int pse, int nr_cap
         why = ST_OBJLIM;
     const Cand best = wave_best<0>(cc);
     if (why == ST_RUN && best.idx == 0) why = ST_P0;
+    if (why == ST_RUN && list_full(nr, nr_cap, m)) why = ST_CAP;
     const bool reset = (why == ST_RUN && pricing == PT_PSE && ts.refct == 0);
     if (why != ST_RUN) {
         // (every block agrees: the state it decided on is not stored until
@@ -1019,13 +1052,16 @@ __global__ void __launch_bounds__(1024) k_dual_row(SpxDev d, int pse, int nr_cap
         }
         return;
     }
-    if (lead) {
+    // the lead block patches what it reads of the header like every other
+    // block, so the pending change of basis needs no block barrier here: its
+    // first thread stores the entries further down (finish_arrays_wave0).
+    // Only the reference-space reset, which reads the whole header, keeps
+    // the barriers of finish_arrays
+    if (lead && reset) {
         finish_arrays(d, fin);
-        if (reset) {
-            reset_refsp_dev(d, 1, false);     // refsp := basic variables, gamma := 1
-            for (int l = threadIdx.x; l < n; l += blockDim.x) d.wpos[l] = -1;
-            if (threadIdx.x == 0) st->nwl = 0;
-        }
+        reset_refsp_dev(d, 1, false);     // refsp := basic variables, gamma := 1
+        for (int l = threadIdx.x; l < n; l += blockDim.x) d.wpos[l] = -1;
+        if (threadIdx.x == 0) st->nwl = 0;
     }
     const int p = best.idx, kp = best.aux;
     const int ns = nr + (kp <= m ? 1 : 0);
@@ -1086,6 +1122,8 @@ __global__ void __launch_bounds__(1024) k_dual_row(SpxDev d, int pse, int nr_cap
             if (pse && !reset) ref2 = f2 != 0 && !(fin.pend && fin.rclr && idx + 1 == fin.kp);
         }
     }
+    // (wave 0 holds its header loads by now; the other waves use none)
+    if (lead && !reset && threadIdx.x == 0) finish_arrays_wave0(d, fin);
     double acc = 0.0;
 #pragma unroll
     for (int u = 0; u < NP; ++u)
@@ -1262,6 +1300,7 @@ __global__ void __launch_bounds__(256) k_dual_col(SpxDev d, int pse, int nr_cap,
         why = ST_OBJLIM;
     const Cand best = wave_best<0>(cc);
     if (why == ST_RUN && best.idx == 0) why = ST_P0;
+    if (why == ST_RUN && list_full(nr, nr_cap, m)) why = ST_CAP;
     const bool reset = (why == ST_RUN && pricing == PT_PSE && ts.refct == 0);
     // every block passes the entry gate before block 0 stores the state
     // (gk_device.h); the header arrays it changes early are patched below
@@ -1533,6 +1572,16 @@ __global__ void __launch_bounds__(256) k_dual_ratio(SpxDev d, int gn, int tiles_
     // (st->delta still holds the pending pivot's until block 0 below)
     RatioIn rin = ratio_in(st);
     if (rowpath == 1) rin.delta = st->ob_delta;
+    // block 0's first wave applies k_dual_row's outbox below: what that needs
+    // is loaded here, with the rest of trip 1 (behind the stop test it was a
+    // trip of its own, which the wave's pass-1 choice waited for)
+    const bool outbox = rowpath == 1 && blockIdx.x == 0 && threadIdx.x < 64;
+    FinishIn obf = {};
+    int ob_p = 0, ob_kp = 0, ob_ns = 0, ob_reset = 0;
+    if (outbox) {
+        obf = finish_load(d);
+        ob_p = st->ob_p; ob_kp = st->ob_kp; ob_ns = st->ob_ns; ob_reset = st->ob_reset;
+    }
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int jc = min(j, n - 1);
     // unconditional loads at clamped indices, selected afterwards (no load
@@ -1590,17 +1639,15 @@ __global__ void __launch_bounds__(256) k_dual_ratio(SpxDev d, int gn, int tiles_
         __syncthreads();
         big = fmax(fmax(rbig[0], rbig[1]), fmax(rbig[2], rbig[3]));
     }
-    if (rowpath == 1 && blockIdx.x == 0 && threadIdx.x == 0) {
+    if (outbox && threadIdx.x == 0) {
         // k_dual_row's outbox: the pending pivot's counters (finish_apply's
         // scalar half, from the state every block of k_dual_row read), then
         // the new pivot — no other block of this launch reads these fields
-        const FinishIn f = finish_load(d);
-        const int ob_p = st->ob_p, ob_kp = st->ob_kp, ob_ns = st->ob_ns, ob_reset = st->ob_reset;
-        const double ob_delta = st->ob_delta;
-        finish_scalars(d, f, ob_reset != 0);
+        // (stores only: the operands came with trip 1)
+        finish_scalars(d, obf, ob_reset != 0);
         st->p = ob_p;
         st->kp = ob_kp;
-        st->delta = ob_delta;
+        st->delta = rin.delta;
         st->ns = ob_ns;
         st->dinf = 0;
     }
@@ -2580,6 +2627,11 @@ __global__ void __launch_bounds__(1024) k_dual_update(SpxDev d, int gn, int ncb,
     const int kold = rowlane ? kold_l : 1;
     if (!rowlane) { bb = 0.0; g = 0.0; }
     if (!colth) { cb = 0.0; tri = 0.0; hkj = 1; }
+    // the inv(B) entries depend on the list alone, not on the entering
+    // choice: issued here, in flight under the choice below
+    double bv[GM];
+#pragma unroll
+    for (int u = 0; u < GM; ++u) bv[u] = Bv[(size_t)min(max(c0[u], 0), m - 1) * ldb + rc];
     TPH(3, 0);
     const double gsum = (NRHS == 2 && w == 0) ? wsum(pin.g) : 0.0;
     // ---- the entering choice (every wave)
@@ -2590,11 +2642,10 @@ __global__ void __launch_bounds__(1024) k_dual_update(SpxDev d, int gn, int ncb,
     // (issued before the stop tests; addresses clamped)
     const bool hdense = !SP && kqc > m;
     const double *__restrict__ hcolv = d.A.A + (size_t)(hdense ? kqc - m - 1 : 0) * d.A.lda;
-    double bv[GM], xa[GM], xb[GM];
+    double xa[GM], xb[GM];
 #pragma unroll
     for (int u = 0; u < GM; ++u) {
         const int ca = min(max(c0[u], 0), m - 1);
-        bv[u] = Bv[(size_t)ca * ldb + rc];
         xa[u] = SP ? 0.0 : hcolv[ca];
         xb[u] = (NRHS == 2) ? d.work[ca] : 0.0;
     }
@@ -3221,9 +3272,10 @@ void dual_iteration2(hipStream_t s, const SpxDev &d, const DualPlan &pl, hipEven
     } else {
         const bool tgrid = !pl.rigorous && d.A.dense && m >= 1024;
         if (tgrid && pl.panel)
-            hipLaunchKernelGGL(k_dual_top_grid<1>, dim3(cdiv(m, 256)), dim3(256), 0, s, d, pl.panel, pl.panel_age);
+            hipLaunchKernelGGL(k_dual_top_grid<1>, dim3(cdiv(m, 256)), dim3(256), 0, s, d, pl.panel, pl.panel_age,
+                               pl.nr_cap);
         else if (tgrid)
-            hipLaunchKernelGGL(k_dual_top_grid<0>, dim3(cdiv(m, 256)), dim3(256), 0, s, d, 0, pl.panel_age);
+            hipLaunchKernelGGL(k_dual_top_grid<0>, dim3(cdiv(m, 256)), dim3(256), 0, s, d, 0, pl.panel_age, pl.nr_cap);
         else
             hipLaunchKernelGGL(k_dual_top, dim3(1), dim3(TOP_WG), 0, s, d, pl.rowpath, pl.nr_cap);
         if (pl.rigorous) refine_rho_dev(s, d);

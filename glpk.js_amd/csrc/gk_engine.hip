@@ -2373,7 +2373,19 @@ int Spx::batch(int K, int rigorous)
             int g = std::max(64, x / 8);
             return std::min(cap, (x + g - 1) / g * g);
         };
-        DualPlan pl = dual_plan(d, bucket(hs.nr + K + 1, m), bucket(hs.nwl + K + 1, n), pse, rigorous);
+        // the cap of the list follows the list, not the budget: nr moves by
+        // far less than one per pivot, and a cap sized for K more entries
+        // loses the fused update (nr_cap + 2 <= 256) and widens every
+        // speculative list load long before the list needs it.  A batch that
+        // does reach its cap stops with ST_CAP and is planned again
+        // (run_dual).  GK_PLAN_SLACK (read per call: tests switch it) is the
+        // slack; at least 1, so the first pivot of a batch always runs
+        const char *es = std::getenv("GK_PLAN_SLACK");
+        const int slack = std::max(1, es ? std::atoi(es) : 32);
+        int nr_cap = std::min(bucket(hs.nr + slack, m), bucket(hs.nr + K + 1, m));
+        // the bucket that crosses the fused update's limit is clipped to it
+        if (nr_cap > DUAL_UPDATE_NR_MAX && hs.nr + slack <= DUAL_UPDATE_NR_MAX) nr_cap = DUAL_UPDATE_NR_MAX;
+        DualPlan pl = dual_plan(d, nr_cap, bucket(hs.nwl + K + 1, n), pse, rigorous);
         pl.sparse = f->sparse ? 1 : 0;
         // profiling launches eagerly: event-record nodes inside captured
         // graphs are not timed by every HIP runtime this library may bind to
@@ -2582,7 +2594,8 @@ void Spx::run_graph_part(const SpxDev &d, const DualPlan &pl, int K, int kind, i
 
 // pivots per device batch: doubled while batches end on their budget, back
 // to the minimum after any other stop (a stop drains the rest of the batch)
-static int next_batch(int k, int why) { return why == ST_BATCH ? std::min(2 * k, 64) : 8; }
+// (a stop on the plan's cap is no trouble: the size stays)
+static int next_batch(int k, int why) { return why == ST_BATCH ? std::min(2 * k, 64) : (why == ST_CAP ? k : 8); }
 
 // a batch that would run past the update limit stops inside its graph and
 // drains the rest as gated no-op launches: end it at the re-inversion point
@@ -2791,6 +2804,7 @@ int Spx::run_dual()
         case ST_BATCH:
         case ST_PHASE:
         case ST_OBJLIM:
+        case ST_CAP:        // the list reached the plan's cap: the next batch is planned from the new nr
             break;
         case ST_REFACT:
             binv_st = 0;

@@ -42,7 +42,11 @@ enum : int {
     ST_DCHK = 8,      // primal: cbar[q] disagrees with re-evaluated d_q
     ST_REFACT = 9,    // update limit reached: re-invert before the next pivot
     ST_REFSP = 10,    // PSE reference space must be reset (refct == 0)
+    ST_CAP = 11,      // dual: the dense-column list reached the batch plan's cap (nr_cap); re-plan and go on
 };
+// k_dual_update holds the active columns of inv(B) in registers: at most 256
+// slots for ns + 1 <= nr_cap + 2 entries, so the largest cap it serves
+constexpr int DUAL_UPDATE_NR_MAX = 254;
 // the gate mode of the end-of-call epilogue's kernels (GATE, gk_device.h)
 constexpr int EPI_GATE = 0x100;
 
